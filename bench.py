@@ -7,7 +7,14 @@ n=512, fp32 complex) that is ALREADY RESIDENT IN HBM when the timed region start
 sector of the sweep has its own 8 MiB of device memory (2.95 GiB per sweep, >> the 256 MiB
 Infinity Cache), so re-reads cannot be served on-die.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--sectors S] [--no-cpu-baseline] [--no-end-to-end]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--sectors S] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-end-to-end] [--no-extras]]
+
+A plain run sets up, settles and warms up, times K steps, writes the last step's products when --dump-outputs is given
+(DIR/zdb.npy, DIR/zdr.npy: [sector][gate] float32 in dB, Zdb without gate 0, whose range is 0 and whose Zdb is -inf by
+definition; the same synthetic input every run) and prints the headline line.
+Everything else below (`achieved_hbm_GBps`, `spot_check_vs_oracle`, `roofline`, `single_sector`, wire formats, shape B,
+end to end, caller's stream, CPU baseline) needs --full.
 
 N > 1 is launched by the driver with torch.distributed.run, one rank per GPU; sectors are
 sharded by rank with NO data-path collective (weak scaling: every GPU owns a full sweep);
@@ -125,6 +132,29 @@ def cpu_baseline(m=1024, n=512):
                       "oracle/radar_oracle.c fp32 port" % ("/".join(str(r["sectors"]) for _, r in runs.values()), t16, physical)}
 
 
+DUMP_LIMIT_BYTES = 60 << 20      # --dump-outputs: all files of all ranks together (under 64 MB)
+
+
+def dump_outputs(out_dir, zdb_zdr, rank, world):
+    """--dump-outputs: the last timed step's products as a caller of wrp_process_batch_device receives them ([sector][gate][Zdb,
+    Zdr], dB) as two float32 arrays: DIR/zdb.npy [sector][gate 1 ..] and DIR/zdr.npy [sector][gate] (rank r > 0: zdb_rank<r>.npy,
+    zdr_rank<r>.npy).  Gate 0 lies at range 0: its Zdb is log10(0) = -inf for every input (smoke() checks it), so zdb.npy starts
+    at gate 1 and every value written is finite for a correct build.  Beyond this rank's share of DUMP_LIMIT_BYTES a fixed,
+    seeded sample of sectors is written instead, their indices in the sweep beside it (sectors*.npy, float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if rank == 0 else "_rank%d" % rank
+    zdb_zdr = np.asarray(zdb_zdr, np.float32)
+    budget = DUMP_LIMIT_BYTES // max(world, 1) - 3 * 4096    # less the .npy headers
+    per_sector = zdb_zdr[0].nbytes - 4 + 8                   # its products without gate 0's Zdb, and its float64 index
+    if len(zdb_zdr) * per_sector > budget:
+        keep = np.sort(np.random.default_rng(0x0D5E).choice(len(zdb_zdr), budget // per_sector, replace=False))
+        zdb_zdr = zdb_zdr[keep]
+        np.save(os.path.join(out_dir, "sectors%s.npy" % sfx), keep.astype(np.float64))
+    np.save(os.path.join(out_dir, "zdb%s.npy" % sfx), np.ascontiguousarray(zdb_zdr[:, 1:, 0]))
+    np.save(os.path.join(out_dir, "zdr%s.npy" % sfx), np.ascontiguousarray(zdb_zdr[:, :, 1]))
+
+
 class RankControl:
     """Barrier and MAX over the ranks of one node through torch.distributed's TCP store (the launcher's own store under
     torch.distributed.run, else one that rank 0 hosts on MASTER_ADDR:MASTER_PORT)."""
@@ -185,10 +215,17 @@ def main():
                     help="A: the 00iq.altb shape 1024 x 512 (BASELINE metric); B: configs[4]'s 2048 range gates x 128 pulses")
     ap.add_argument("--settle", type=float, default=SETTLE_S,
                     help="seconds of untimed launches before the warm-up steps (profiling passes shorten it)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else: spot check against the oracle, roofline, single-sector latency, "
+                         "wire formats, shape B, end to end, caller's stream, CPU baseline (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; same inputs every run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the single-sector latency and wire-format sections (profiling passes)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != args.gpus:
@@ -323,6 +360,42 @@ def main():
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     eng.check()                               # a fused launch that gave up would be reported here
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out.cpu().numpy(), rank, world)
+
+    c2 = wrp_amd.WrpConfig()
+    eng.lib.wrp_get_config(eng.handle, c2)
+    fused = (c2.flags & (wrp_amd.FLAG_TWO_KERNELS | wrp_amd.FLAG_GENERIC_KERNELS)) == 0 and S >= wrp_amd.FUSED_MIN_SECTORS
+    total_sectors = world * S * args.steps
+    line = {
+        "metric": "sectors/sec + achieved HBM GB/s on in/00iq.altb shape, 1/2/4/8 GPUs",
+        "value": round(total_sectors / elapsed, 1), "unit": "sectors/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": (f"00iq.altb shape (C=2, m=1024, n=512, fp32 complex), {S}-sector elevation "
+                                f"sweep per GPU per step, device-resident") if args.shape == "A" else
+                               (f"shape B = BASELINE configs[4] (C=2, m=2048 range gates, n=128 pulses, fp32 complex), {S} sectors "
+                                f"per GPU per step, device-resident"), "sectors_per_step_per_gpu": S,
+                   "parallelism": f"sector-sharded x{world}, no collective (barrier + MAX of the elapsed time over a TCP store)",
+                   "launch": "fused" if fused else "two kernels", "untimed_settle_s": args.settle,
+                   # a7 (read.cc:290-301) in the timed launch, said in so many words (VERDICT r04)
+                   "ma_stage": "row sum as the DC bin of the circular moving average: S = (sum of the taps) x (sum |.|^2); the stage "
+                               "08pow itself (direct causal circular 7-tap) is formed by the dump instantiations only -- every ma_count "
+                               "stage-tested in tests/test_gpu_batches.py; forming it in the timed launch costs +0.97 % (1024 x 512), "
+                               "+0.59 % (wire format), +0.27 % (2048 x 128): profiles/r04/ab_rowsum_dc_bin.log"},
+    }
+
+    def finish():
+        eng.close()
+        if ctl is not None:
+            ctl.barrier()
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+
+    if not args.full:
+        return finish()
 
     # correctness spot check on what was just computed (first and last sector of the sweep)
     ok = True
@@ -341,9 +414,6 @@ def main():
     algo = eng.algorithmic_bytes
     t_sector = ms_total * 1e-3 / (iters * S)
     achieved = algo / t_sector / 1e9
-    c2 = wrp_amd.WrpConfig()
-    eng.lib.wrp_get_config(eng.handle, c2)
-    fused = (c2.flags & (wrp_amd.FLAG_TWO_KERNELS | wrp_amd.FLAG_GENERIC_KERNELS)) == 0 and S >= wrp_amd.FUSED_MIN_SECTORS
     per_launch = S if fused else min(S, c2.max_batch)
     launches = 1 if fused else -(-S // c2.max_batch)
     kernel = (("fused_chain_1024x512" if args.shape == "A" else "fused_chain_2048x128") +
@@ -560,31 +630,13 @@ def main():
         caller["fused_fallbacks"] = eng.fused_fallbacks
         del d_raw, d_o
 
-    total_sectors = world * S * args.steps
-    line = {
-        "metric": "sectors/sec + achieved HBM GB/s on in/00iq.altb shape, 1/2/4/8 GPUs",
-        "value": round(total_sectors / elapsed, 1), "unit": "sectors/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": (f"00iq.altb shape (C=2, m=1024, n=512, fp32 complex), {S}-sector elevation "
-                                f"sweep per GPU per step, device-resident") if args.shape == "A" else
-                               (f"shape B = BASELINE configs[4] (C=2, m=2048 range gates, n=128 pulses, fp32 complex), {S} sectors "
-                                f"per GPU per step, device-resident"), "sectors_per_step_per_gpu": S,
-                   "parallelism": f"sector-sharded x{world}, no collective (barrier + MAX of the elapsed time over a TCP store)",
-                   "launch": "fused" if fused else "two kernels", "untimed_settle_s": args.settle,
-                   # a7 (read.cc:290-301) in the timed launch, said in so many words (VERDICT r04)
-                   "ma_stage": "row sum as the DC bin of the circular moving average: S = (sum of the taps) x (sum |.|^2); the stage "
-                               "08pow itself (direct causal circular 7-tap) is formed by the dump instantiations only -- every ma_count "
-                               "stage-tested in tests/test_gpu_batches.py; forming it in the timed launch costs +0.97 % (1024 x 512), "
-                               "+0.59 % (wire format), +0.27 % (2048 x 128): profiles/r04/ab_rowsum_dc_bin.log"},
+    line.update({
         "achieved_hbm_GBps": round(world * achieved, 1),
         "spot_check_vs_oracle": ok,
         "single_sector_latency_us": single["submit_wait_pinned_us"] if single else None,
         "single_sector": single,
         "roofline": roofline,
-    }
+    })
     if wire is not None:
         line["wire_format_input"] = wire
     if shape_b is not None:
@@ -595,11 +647,7 @@ def main():
         line["caller_stream"] = caller
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(m, n)
-    eng.close()
-    if ctl is not None:
-        ctl.barrier()
-    if rank == 0:
-        print(json.dumps(line), flush=True)
+    finish()
 
 
 if __name__ == "__main__":

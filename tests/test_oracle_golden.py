@@ -147,21 +147,25 @@ def test_host_codecs_match_reference_vectors(oracle, golden):
                     assert all(oracle.dim3_at_depth(w, h, x, y, dp) == z["dim3"][dp, y, x] for x in range(w))
 
 
-def test_live_reference_host_lib_if_present(oracle):
-    """When oracle/_ref/libref_host.so travelled with the tree, fuzz our restatement against it."""
+def test_live_reference_host_lib_if_present(oracle, golden):
+    """Fuzz our restatement against the reference's Sector::fromByteArray: its answer on 16 x 8 random samples is stored
+    (tests/golden/ref_host_sector_fuzz.npz, tools/make_golden.py); when oracle/_ref/libref_host.so was built, the live
+    library must give that same answer."""
     import ctypes as C
-    ref = oracle.ref_host()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (no /root/reference at build time)")
-    rng = np.random.default_rng(3)
-    sw, sa = 16, 8
-    raw = rng.integers(0, 256, 12 * sw * sa, dtype=np.uint8)
-    hh = np.empty(2 * sw * sa, np.int16); vv = np.empty_like(hh); vh = np.empty_like(hh)
-    buf = (C.c_char * raw.size).from_buffer_copy(raw.tobytes())
-    sp = C.POINTER(C.c_short)
-    ref.ref_sector_from_bytes(buf, sw, sa, hh.ctypes.data_as(sp), vv.ctypes.data_as(sp), vh.ctypes.data_as(sp))
+    z = golden("ref_host_sector_fuzz.npz")
+    sw, sa = int(z["sweeps"]), int(z["samples"])
+    raw = np.random.default_rng(3).integers(0, 256, 12 * sw * sa, dtype=np.uint8)
+    assert np.array_equal(raw, z["raw"])
+    want = (z["hh"], z["vv"], z["vh"])
     o = oracle.sector_from_bytes(raw, sw, sa)
-    assert all(np.array_equal(a, b) for a, b in zip(o, (hh, vv, vh)))
+    assert all(np.array_equal(a, b) for a, b in zip(o, want))
+    ref = oracle.ref_host()
+    if ref is not None:
+        hh = np.empty(2 * sw * sa, np.int16); vv = np.empty_like(hh); vh = np.empty_like(hh)
+        buf = (C.c_char * raw.size).from_buffer_copy(raw.tobytes())
+        sp = C.POINTER(C.c_short)
+        ref.ref_sector_from_bytes(buf, sw, sa, hh.ctypes.data_as(sp), vv.ctypes.data_as(sp), vh.ctypes.data_as(sp))
+        assert all(np.array_equal(a, b) for a, b in zip((hh, vv, vh), want))
 
 
 def test_result_framing(oracle):

@@ -17,6 +17,8 @@ numeric inputs and expected outputs -- never reference source text:
   ref_sum_out.npz       out/sum.out: 16x8 input and its per-row tree-reduction result
   ref_host_codecs.npz   vectors produced by the reference's sector.cpp / floats.c /
                         dimension.cpp compiled into oracle/_ref/libref_host.so
+  ref_host_sector_fuzz.npz  Sector::fromByteArray of 16 x 8 random 12-byte samples (seed 3), the same
+                        compiled code: what tests/test_oracle_golden.py fuzzes the restatement with
 """
 import ctypes as C
 import os
@@ -112,8 +114,20 @@ def main():
     np.savez(f"{OUT}/ref_host_codecs.npz", raw=raw, sweeps=sweeps, samples=samples,
              hh=hh, vv=vv, vh=vh, floats=fl, floats_be=ab, dim4=d4, dim3=d3,
              dim_whcd=np.array([w, h, c, d]))
+    sector_fuzz(ref)
     for f in sorted(os.listdir(OUT)):
         print(f"{f:32s} {os.path.getsize(os.path.join(OUT, f)):9d} B")
+
+
+def sector_fuzz(ref):
+    rng = np.random.default_rng(3)
+    sweeps, samples = 16, 8
+    raw = rng.integers(0, 256, 12 * sweeps * samples, dtype=np.uint8)
+    hh = np.empty(2 * sweeps * samples, np.int16); vv = np.empty_like(hh); vh = np.empty_like(hh)
+    buf = (C.c_char * raw.size).from_buffer_copy(raw.tobytes())
+    sp = C.POINTER(C.c_short)
+    ref.ref_sector_from_bytes(buf, sweeps, samples, hh.ctypes.data_as(sp), vv.ctypes.data_as(sp), vh.ctypes.data_as(sp))
+    np.savez(f"{OUT}/ref_host_sector_fuzz.npz", raw=raw, sweeps=sweeps, samples=samples, hh=hh, vv=vv, vh=vh)
 
 
 if __name__ == "__main__":

@@ -13,8 +13,8 @@ cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/$R; mkdir -p $OUT profiles/$R
 T="--steps 3 --warmup 2 --settle 0.01 --sectors 360 --no-cpu-baseline --no-end-to-end --no-extras"
 if phase pmc; then
-echo "== kernel trace A"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_A -- python3 bench.py --no-cpu-baseline --no-end-to-end --no-extras > $OUT/trace_A.log 2>&1
-echo "== kernel trace B"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_B -- python3 bench.py --shape B --no-cpu-baseline --no-end-to-end --no-extras > $OUT/trace_B.log 2>&1
+echo "== kernel trace A"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_A -- python3 bench.py --full --no-cpu-baseline --no-end-to-end --no-extras > $OUT/trace_A.log 2>&1
+echo "== kernel trace B"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_B -- python3 bench.py --full --shape B --no-cpu-baseline --no-end-to-end --no-extras > $OUT/trace_B.log 2>&1
 echo "== PMC passes A"; tools/profile_pmc.sh $OUT/pmc > $OUT/pmc.log 2>&1; tail -5 $OUT/pmc.log
 python3 tools/make_traffic.py $OUT/pmc/summary.txt 360 fused_chain_1024x512 > $OUT/traffic.json && cp $OUT/traffic.json profiles/$R/traffic.json
 python3 tools/make_busy.py $OUT/pmc/summary.txt fused_chain_1024x512 > $OUT/busy.json && cp $OUT/busy.json profiles/$R/busy.json
@@ -37,8 +37,8 @@ fi
 if phase bench; then
 echo "== floors (the launches without their input)"; tools/make_floor.sh run $R > $OUT/floor.log 2>&1; tail -2 $OUT/floor.log
 cp $OUT/floor.json $OUT/floor_B.json profiles/$R/ 2>/dev/null
-echo "== bench B with the records of this build"; python3 bench.py --shape B --no-cpu-baseline > $OUT/bench_B.json 2> $OUT/bench_B.err; tail -c 300 $OUT/bench_B.json
-echo "== bench A with the records of this build"; python3 bench.py > $OUT/bench_A.json 2> $OUT/bench_A.err; cat $OUT/bench_A.json
+echo "== bench B with the records of this build"; python3 bench.py --full --shape B --no-cpu-baseline > $OUT/bench_B.json 2> $OUT/bench_B.err; tail -c 300 $OUT/bench_B.json
+echo "== bench A with the records of this build"; python3 bench.py --full > $OUT/bench_A.json 2> $OUT/bench_A.err; cat $OUT/bench_A.json
 echo "== the driver's command"; python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err; tail -c 300 $OUT/bench_driver_command.json
 fi
 # keep the merged directory small: the stats tables, not the raw traces
